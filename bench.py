@@ -10,6 +10,8 @@ A step = one pass of the hot path over one synthetic batch resident in HBM: ResN
 Workload = BASELINE.json configs[1]: 512x512, batch 16 per GPU (weak scaling), 9 fine / 4 coarse classes, fp32.
 Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events on the launch stream over one extra
 instrumented step; `cpu_baseline` times the CPU oracle (oracle.step.OracleTrainer, kind "port") on a bounded sample.
+`--dump-outputs DIR` writes what the last timed step left its caller as DIR/<name>.npy (see dump_outputs), so that two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -17,15 +19,17 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-FP32_MFMA_PEAK_TF = 157.3        # /opt/skills/guides/MI355X_MICROARCH.md, chip-level parameters
+FP32_MFMA_PEAK_TF = 157.3        # MI355X chip-level parameters
 BF16_MFMA_PEAK_TF = 2500.0       # dense bf16 MFMA peak; the x6 conv path spends 6 bf16 MFMA flops per fp32 flop
 HBM_PEAK_GBS = 8000.0
 CFG = dict(depth=50, n_fine=9, coarse_to_fine_map=[[0, 3], [4, 6], [7], [8]], size=512, batch=16)
+DUMP_SAMPLE = 1 << 21            # --dump-outputs: at most this many elements per array (8 MiB of f32; the whole dump stays < 64 MB)
 
 
 def csrc_sha():
@@ -49,6 +53,39 @@ def make_inputs(batch, rank, dev):
     """The synthetic batch of rank `rank`: seed = rank, resident on `dev`."""
     from seghiero_amd.synthetic import make_batch
     return make_batch(batch, CFG["size"], CFG["n_fine"], seed=rank, device=dev)
+
+
+def _sample(flat):
+    """A fixed, seeded sample of a 1-D tensor (the same sorted positions for every build and run), or all of it if small."""
+    n = flat.numel()
+    if n <= DUMP_SAMPLE:
+        return flat
+    idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    return flat[torch.from_numpy(idx).to(flat.device)]
+
+
+def dump_outputs(tr, loss, out_dir):
+    """What the timed path hands its caller after its last step, as out_dir/<name>.npy: the loss it returned (f32 scalar) and,
+    per module, `<module>_state` (floating state_dict entries: parameters + BatchNorm running statistics), `<module>_grad` (the
+    weight gradients of that step) and `<module>_momentum` (the SGD momentum buffers).  Each is the concatenation of its tensors
+    in state_dict / parameter order, flattened in their logical (NCHW) shapes whatever the memory layout, as f32; arrays above
+    DUMP_SAMPLE elements are a fixed seeded sample of it.  -> {name: shape}"""
+    def flat(ts):
+        return torch.cat([t.detach().float().reshape(-1) for t in ts])
+
+    arrays = {"loss": loss.detach().float().reshape(())}
+    for name, m in tr.modules().items():
+        params = list(m.parameters())
+        moms = [tr.optimizer.state.get(p, {}).get("momentum_buffer") for p in params]
+        arrays[name + "_state"] = _sample(flat(v for v in m.state_dict().values() if v.is_floating_point()))
+        arrays[name + "_grad"] = _sample(flat(torch.zeros_like(p) if p.grad is None else p.grad for p in params))
+        arrays[name + "_momentum"] = _sample(flat(torch.zeros_like(p) if v is None else v for p, v in zip(params, moms)))
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= 64_000_000
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def cpu_baseline(seconds_budget=30.0):
@@ -90,7 +127,12 @@ def main():
     ap.add_argument("--syncbn", action="store_true",
                     help="N > 1: BatchNorm statistics over all ranks (BASELINE configs[2] variant; default = per-rank statistics, "
                          "the weak-scaling setting of SURVEY 8d)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss; per module a seeded sample of the state, "
+                         "weight gradients and momentum buffers) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from seghiero_amd import ddp, ops
 
@@ -136,6 +178,9 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         ddp.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t)
+    dumped = None
+    if args.dump_outputs and rank == 0:         # before the untimed steps below move the weights on
+        dumped = dump_outputs(tr, loss, args.dump_outputs)
     loss_val = float(loss)
     # host side of a step: Python + launch time with the device idle at the start (nothing can block on a full queue)
     host_ms = []
@@ -255,6 +300,8 @@ def main():
         "loss": round(loss_val, 5), "loss_step0": None if loss0 is None else round(float(loss0), 6),
         "host_ms_per_step": round(sorted(host_ms)[1], 2), "bf16_compute_mode": bf16_mode, "roofline": roof, "roofline_units": roof_units, "kernel_ms_per_step": breakdown,
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
     print(json.dumps(out), flush=True)
