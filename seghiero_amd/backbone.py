@@ -66,16 +66,6 @@ def _stage(kind, cin, width, n, stride):
     return nn.Sequential(*blocks), cout
 
 
-# Residual-block form of the fused BatchNorm backward (the next block's first dgrad epilogue masks with this block's output and
-# emits its bn3 statistics).  Measured at the headline shape (same-box A/B): while the epilogue spilled 85 registers this cost more
-# (+1.6 ms of dgrad) than the statistics pass it replaces (-0.7 ms); with the epilogue processed in row-group chunks (no spills) it
-# wins: dgrad +0.6 ms, statistics pass -1.0 ms, step 33.94 -> 33.45 ms -- on by default.
-BNB_RESIDUAL = __import__("os").environ.get("SEGHIERO_BNB_RESIDUAL", "1") != "0"
-# The gradient a stage output receives from outside the trunk (c1 <- decoder, c3 <- aux head) is summed by the first dgrad epilogue of the
-# next stage's first block instead of an axpy pass over the 268 MB / 67 MB tensor: same-box A/B 33.00 -> 32.85 ms per step.
-STAGE_GRAD_IN_EPILOGUE = __import__("os").environ.get("SEGHIERO_STAGE_GRAD_EPI", "1") != "0"
-
-
 # ----------------------------------------------------------------------------- hand-scheduled fwd / bwd
 def _block_fwd(blk, x, training):
     chain = blk.chain()
@@ -161,7 +151,7 @@ class _BackboneFn(torch.autograd.Function):
             mod.__dict__["_stem_wpad"] = (wkey, wpad)
         # act_dtype = torch.bfloat16 (training only): the trunk's raw conv outputs and block outputs are STORED as bf16 -- half the
         # bytes of every activation read and write; arithmetic, BatchNorm statistics and gradients stay fp32 (BASELINE configs[4])
-        stored = mod.act_dtype if (training and L.FUSE_BN and ops.CONV_IMPL == "x6") else torch.float32
+        stored = mod.act_dtype if training else torch.float32
         # compute_dtype = torch.bfloat16 (with bf16 storage): ONE bf16 MFMA product per tile on operands rounded once to bf16 in the
         # loaders (csrc/conv_b16.hip) instead of the fp32-accurate six-product plan; stage outputs are then handed on as bf16 tensors
         compute = mod.compute_dtype if stored == torch.bfloat16 else torch.float32
@@ -217,18 +207,23 @@ class _BackboneFn(torch.autograd.Function):
                     d = g
                 else:
                     if isinstance(d, L.GradPack):
-                        raise SegHieroHipError("a packed gradient cannot take a stage gradient (STAGE_GRAD_IN_EPILOGUE covers this case)")
+                        raise SegHieroHipError("a packed gradient cannot take a stage gradient (the next stage's first dgrad epilogue sums it)")
                     d = ops.f32(d)
                     ops._call("sh_axpy", d.data_ptr(), _dense(g).data_ptr(), 1.0, d.numel(), ops._st())
             if d is None:
                 continue
             prev_rec = None
-            if BNB_RESIDUAL and idx > 0 and blocks[idx - 1][0] == li and blk.downsample is None:
-                prev_rec = saved[idx - 1][0][-1]                      # previous block of the same stage feeds this one directly
+            if idx > 0 and blocks[idx - 1][0] == li and blk.downsample is None:
+                # previous block of the same stage feeds this one directly: residual-block form of the fused BatchNorm backward (this
+                # block's first dgrad epilogue masks with that block's output and emits its bn3 statistics).  Measured at the headline
+                # shape (same-box A/B against a separate statistics pass): with the epilogue processed in row-group chunks (no spills)
+                # dgrad +0.6 ms, statistics pass -1.0 ms, step 33.94 -> 33.45 ms
+                prev_rec = saved[idx - 1][0][-1]
             extra = None
-            if STAGE_GRAD_IN_EPILOGUE and idx > 0 and blocks[idx - 1][0] != li and blk.downsample is not None and douts[blocks[idx - 1][0]] is not None:
+            if idx > 0 and blocks[idx - 1][0] != li and blk.downsample is not None and douts[blocks[idx - 1][0]] is not None:
                 # first block of a stage: the previous stage's own output gradient (c1 from the decoder, c3 from the aux head) rides in
-                # this block's first dgrad epilogue instead of a separate read-modify-write pass over the stage output
+                # this block's first dgrad epilogue instead of a separate read-modify-write (axpy) pass over the 268 MB / 67 MB stage
+                # output: same-box A/B 33.00 -> 32.85 ms per step
                 lp = blocks[idx - 1][0]
                 extra = L.grad_as_nhwc_padded(douts[lp], douts[lp].shape[1])
                 summed.add(lp)

@@ -74,7 +74,7 @@ class DepthwiseSeparableASPPModule(nn.Module):
                                                                     dilation=d, padding=d, bias=False))
 
 
-ASPP_GROUPED = __import__("os").environ.get("SEGHIERO_ASPP_GROUPED", "1") != "0"
+ASPP_GROUPED = True       # False: the branches one by one (the reference path of the grouped-unit tests)
 
 
 def _aspp_branches_grouped(aspp, c4, cat, A, training, R, c4b=None):
@@ -93,7 +93,7 @@ def _aspp_branches_grouped(aspp, c4, cat, A, training, R, c4b=None):
     Fills R["b0"], R["pw<i>"] and R["dw<i>"] / R["dwc<i>"]; False = geometry not eligible (the caller runs the branches one by one)."""
     n, cin, h, w = c4.shape
     nbr = len(aspp.dilations)
-    if not (ASPP_GROUPED and training and L.FUSE_BN and ops.CONV_IMPL == "x6" and not ops._sync_on() and A % 128 == 0 and cin % 16 == 0
+    if not (ASPP_GROUPED and training and not ops._sync_on() and A % 128 == 0 and cin % 16 == 0
             and nbr <= 6):
         return False
     dev = c4.device
@@ -161,7 +161,7 @@ class _HeadFn(torch.autograd.Function):
         R = {}
         # bf16 compute mode: the 2048-channel consumers of c4 (projection head, ASPP pointwise convs) read a bf16 copy of it (8 M elements:
         # the trunk hands its stage outputs on as fp32 tensors); pooling, statistics and the dilated depthwise conv keep the fp32 tensor
-        b16 = ops.b16() and training and L.FUSE_BN and mod.act_dtype == torch.bfloat16 and cin % 8 == 0
+        b16 = ops.b16() and training and mod.act_dtype == torch.bfloat16 and cin % 8 == 0
         c4b = c4.to(torch.bfloat16) if b16 else None
         # ---- projection head -> l2-normalised embedding (:12-30)
         proj = mod.proj_head.proj
@@ -199,7 +199,7 @@ class _HeadFn(torch.autograd.Function):
         # act_dtype = torch.bfloat16 (training, strip-walk geometry): the decoder's 128 x 128 tensors -- concat buffer, raw depthwise and
         # pointwise outputs -- are STORED as bf16 like the trunk's (ResNetBackbone.act_dtype; arithmetic / statistics / gradients fp32)
         H1, W1 = (c1.shape[2:] if mod.c1_bottleneck is not None else (h, w))
-        stored = mod.act_dtype if (training and L.FUSE_BN and ops.CONV_IMPL == "x6" and ops.dw_lin_ok((n, A, H1, W1), 1)) else torch.float32
+        stored = mod.act_dtype if (training and ops.dw_lin_ok((n, A, H1, W1), 1)) else torch.float32
         with ops.stored_as(stored):
             if mod.c1_bottleneck is not None:
                 c1 = ops.to_nhwc(c1)

@@ -54,9 +54,6 @@ def bump_bn_counters(bns):
 
 
 # ----------------------------------------------------------------------------- deferred BatchNorm + ReLU
-FUSE_BN = __import__("os").environ.get("SEGHIERO_FUSE_BN", "1") != "0"      # 0: every BatchNorm + ReLU is its own pass (round-1 path)
-
-
 class Lazy:
     """relu(y * scale + shift) of a raw conv output, NOT materialised: the consumer convolution applies it in its loader
     (ops.conv_fprop_aff / conv_wgrad(aff=...)), so conv -> BN -> ReLU -> conv chains never write or re-read the activated
@@ -172,22 +169,22 @@ def _dgrad_as(gdt, rec_x, dy, weight, s, p, d, addend, pack_for):
 
     if isinstance(dy, ops.DeferredDy):
         if pack_for is None:
-            if isinstance(rec_x, Lazy) and FUSE_BN:
+            if isinstance(rec_x, Lazy):
                 g, partials = new(), parts()
                 if ops.conv_dgrad_lin(dy, weight, g, addend=addend, bnb=(rec_x.y, rec_x.coefs, partials)):
                     return GradPack(g, partials)
-            elif not isinstance(rec_x, Lazy):
+            else:
                 dx = new()
                 if ops.conv_dgrad_lin(dy, weight, dx, addend=addend):
                     return dx
         dy = dy.materialize()
-    if pack_for is not None and FUSE_BN and not isinstance(rec_x, Lazy):
+    if pack_for is not None and not isinstance(rec_x, Lazy):
         g, partials = new(), parts()
         if ops.conv_dgrad_bnb(dy, weight, g, pack_for.y, pack_for.coefs, True, partials, s, p, d, addend=addend,
                               out_prev=pack_for.out if pack_for.mask is None else pack_for.mask):
             return GradPack(g, partials)
         return plain(dy, g)
-    if isinstance(rec_x, Lazy) and FUSE_BN:
+    if isinstance(rec_x, Lazy):
         g, partials = new(), parts()
         if ops.conv_dgrad_bnb(dy, weight, g, rec_x.y, rec_x.coefs, True, partials, s, p, d, addend=addend):
             return GradPack(g, partials)
@@ -206,7 +203,7 @@ def cba_fwd(x, weight, geom, bn, relu, training, residual=None, out=None, lazy=F
     ld = ops.pad4(o)
     m = n * ho * wo
     mask = None
-    if not training and ops.FUSE_EVAL and ops.CONV_IMPL == "x6":
+    if not training and ops.FUSE_EVAL:
         # inference: eval-mode BN (+ residual) (+ ReLU) in the conv epilogue; y is never materialised
         coefs = _bn_coefs(bn, None, m, False, o, x.device)
         if out is None:
@@ -218,15 +215,15 @@ def cba_fwd(x, weight, geom, bn, relu, training, residual=None, out=None, lazy=F
         partials = ops.conv_partials(m, o, x.device) if training else None
         _fprop(x, weight, None, y, partials, s, p, d)
         coefs = _bn_coefs(bn, partials, m, training, o, x.device)
-        if lazy and FUSE_BN and training and relu and residual is None and out is None and ops.CONV_IMPL == "x6":
+        if lazy and training and relu and residual is None and out is None:
             out = Lazy(y, coefs)
-        elif lazy and FUSE_BN and training and not relu and residual is None and out is None:
+        elif lazy and training and not relu and residual is None and out is None:
             out = LazyAffine(y, coefs)
         else:
             if out is None:
                 out = ops.new_act(n, o, ho, wo, x.device, ld=ld, zero=ld != o, dtype=ops.stored_dtype())
             # a residual block's output: its backward needs only the ReLU mask of `out` -- kept as a quad mask (1/16 of the bytes)
-            if training and relu and residual is not None and ops.RELU_MASK and FUSE_BN and o % 4 == 0 and ops.CONV_IMPL == "x6":
+            if training and relu and residual is not None and o % 4 == 0:
                 mask = ops.new_relu_mask(n, o, ho, wo, x.device)
             if isinstance(residual, LazyAffine):
                 ops.bn_act(y, coefs, out, relu, residual.y, res_coefs=residual.coefs, mask=mask)
@@ -261,22 +258,19 @@ def cba_bwd(rec, bn, dout, need_dx=True, addend=None, want_dres=False, scatter_i
     # dout may be a GradPack (mask applied, statistics partials done by the consumer's dgrad epilogue).
     mode = 0 if not rec.relu else (1 if rec.has_res else 2)
     # second half of the BatchNorm backward in the loaders of this conv's dgrad / wgrad (1x1 convs): no apply pass, no dy tensor
-    defer = FUSE_BN and scatter_into is None and pack_for is None and ops.lin_ok(rec.x.shape, rec.weight, s, p, d)
+    defer = scatter_into is None and pack_for is None and ops.lin_ok(rec.x.shape, rec.weight, s, p, d)
     dy, dgamma, dbeta, dres = ops.bn_backward(dout, (rec.out if rec.mask is None else rec.mask) if mode == 1 else None, rec.y, rec.coefs,
                                               W(bn), mode, want_dres, defer=defer, grad32=dy32)
     dw = new_grad(rec.weight)
-    if not ops.WGRAD_AFTER_DGRAD:
-        _wgrad(rec.x, dy, dw, s, p, d)
     dx = None
     if scatter_into is not None:
         ops.conv_dgrad(dy, rec.weight, scatter_into, s, p, d, mode=1)
         dx = scatter_into
     elif need_dx:
         dx = _dgrad(rec.x, dy, rec.weight, s, p, d, addend=addend, pack_for=pack_for, grad32=dx32)
-    if ops.WGRAD_AFTER_DGRAD:
-        # enqueued after the dgrad: the side stream then starts this (MFMA-bound) wgrad when the dgrad has finished, i.e.
-        # next to the HBM-bound BatchNorm backward of the previous layer instead of next to another MFMA-bound kernel
-        _wgrad(rec.x, dy, dw, s, p, d)
+    # enqueued after the dgrad: the side stream then starts this (MFMA-bound) wgrad when the dgrad has finished, i.e.
+    # next to the HBM-bound BatchNorm backward of the previous layer instead of next to another MFMA-bound kernel
+    _wgrad(rec.x, dy, dw, s, p, d)
     return dx, dw, dgamma, dbeta, dres
 
 
@@ -296,7 +290,7 @@ def dw_fwd(x, weight, dil, bn, training, lazy=False):
         x = dense(x)
         ops.dwconv_fprop(x, weight, y, partials, dil)
     coefs = _bn_coefs(bn, partials, n * h * w, training, c, x.device)
-    if lazy and FUSE_BN and training and ops.CONV_IMPL == "x6":
+    if lazy and training:
         out = Lazy(y, coefs, grad32=True)              # the depthwise backward kernels take fp32 gradients
     else:
         out = ops.new_act(n, c, h, w, x.device)
@@ -314,7 +308,7 @@ def dw_bwd(rec, bn, dout, dx_accumulate_into=None):
         dout.g = ops.f32(dout.g)
     else:
         dout = ops.f32(dout)
-    dy, dgamma, dbeta, _ = ops.bn_backward(dout, None, rec.y, rec.coefs, W(bn), 2, defer=FUSE_BN and ops.dw_lin_ok(rec.y.shape, rec.dil),
+    dy, dgamma, dbeta, _ = ops.bn_backward(dout, None, rec.y, rec.coefs, W(bn), 2, defer=ops.dw_lin_ok(rec.y.shape, rec.dil),
                                            grad32=True)
     dw = new_grad(rec.weight)
     if isinstance(rec.x, Lazy) and rec.x._out is None:
@@ -327,7 +321,7 @@ def dw_bwd(rec, bn, dout, dx_accumulate_into=None):
     else:
         n, c, h, w = rec.x.shape
         dx = ops.new_act(n, c, h, w, rec.x.device)
-        if isinstance(rec.x, Lazy) and FUSE_BN:
+        if isinstance(rec.x, Lazy):
             # the input is a deferred activation: its BatchNorm backward starts in this dgrad's epilogue (-> GradPack)
             partials = torch.empty((ops.dw_partials_rows(n, h, w), 2, c), device=dx.device, dtype=torch.float32)
             ops.dwconv_dgrad_bnb(dy, rec.weight, dx, rec.x.y, rec.x.coefs, partials, rec.dil)

@@ -4,6 +4,7 @@ Everything here is plumbing: PyTorch provides device memory (the caching allocat
 HIP stream; all arithmetic happens in libseghiero_hip.so.  Activations are logical NCHW tensors whose
 memory is NHWC (``channels_last``), possibly a channel slice of a wider buffer (pixel stride ``ld``).
 """
+import contextlib
 import ctypes
 
 import torch
@@ -11,9 +12,6 @@ import torch
 from ._lib import LIB, SegHieroHipError, status_text
 
 import os
-
-# "x6": fp32-accurate 6 x bf16-split MFMA path (default); "f32": v_mfma_f32_32x32x2_f32 path.
-CONV_IMPL = os.environ.get("SEGHIERO_CONV", "x6")
 
 _PROF = None          # when set (see `profile()`), every C-ABI call is bracketed by HIP events on its launch stream
 
@@ -150,7 +148,7 @@ class compute_as:
 
     def __enter__(self):
         global _B16
-        self.prev, _B16 = _B16, self.on and CONV_IMPL == "x6"
+        self.prev, _B16 = _B16, self.on
 
     def __exit__(self, *exc):
         global _B16
@@ -266,8 +264,6 @@ def _call_fused(name, *args, cost=None, key=None):
 def conv_fprop_aff(x, in_coefs, weight, bias, y, partials, stride, pad, dil):
     """y = conv(relu(x * scale + shift), weight): the producer's train-mode BatchNorm + ReLU applied in the conv's loader
     (in_coefs = the (4, C) coefficient tensor of bn_finalize).  -> False when the geometry has no fused kernel."""
-    if CONV_IMPL != "x6":
-        return False
     n, cin, h, w = x.shape
     o, _, kh, kw = weight.shape
     xp, ldx, xb = pmx(x)
@@ -319,24 +315,17 @@ def conv_fprop(x, weight, bias, y, partials, stride, pad, dil):
         return
     ho, wo = conv_out_hw(h, w, kh, kw, stride, pad, dil)
     m = n * ho * wo
-    x6 = CONV_IMPL == "x6"
-    if (xb or yb) and not x6:
-        raise SegHieroHipError("bf16-stored activations need the x6 convolution path")
-    wptr = w_ohwi(weight).data_ptr()
     cost = (2.0 * m * o * cin * kh * kw, 4.0 * (n * h * w * cin + m * o + o * cin * kh * kw))
-    args = (xp, ldx, wptr, None if bias is None else bias.data_ptr(), yp, ldy,
-            None if partials is None else partials.data_ptr(), n, h, w, cin, o, kh, kw, stride, pad, dil)
-    if x6:
-        ws, nb = _splitk_ws(0, n, h, w, cin, o, kh, kw, stride, pad, dil, 0, x.device)
-        _call("sh_conv_fprop_x6", *args, ws, nb, xb | (yb << 1), _st(), cost=cost, key=_ckey(n, h, w, cin, o, kh, stride, dil))
-    else:
-        _call("sh_conv_fprop", *args, _st(), cost=cost, key=_ckey(n, h, w, cin, o, kh, stride, dil))
+    ws, nb = _splitk_ws(0, n, h, w, cin, o, kh, kw, stride, pad, dil, 0, x.device)
+    _call("sh_conv_fprop_x6", xp, ldx, w_ohwi(weight).data_ptr(), None if bias is None else bias.data_ptr(), yp, ldy,
+          None if partials is None else partials.data_ptr(), n, h, w, cin, o, kh, kw, stride, pad, dil, ws, nb, xb | (yb << 1), _st(),
+          cost=cost, key=_ckey(n, h, w, cin, o, kh, stride, dil))
 
 
-SPLIT_K = os.environ.get("SEGHIERO_SPLITK", "1") != "0"      # debugging knob: 0 = never hand the conv kernels a split-K workspace
+SPLIT_K = True            # False = never hand the conv kernels a split-K workspace (a reference path for the tests)
 
 
-FUSE_EVAL = os.environ.get("SEGHIERO_FUSE_EVAL", "1") != "0"      # inference: BN (+residual) (+ReLU) in the conv epilogue
+FUSE_EVAL = True          # inference: BN (+residual) (+ReLU) in the conv epilogue (False: the training kernels, a test reference)
 
 
 def conv_fprop_act(x, weight, coefs, out, relu, residual, stride, pad, dil):
@@ -538,7 +527,7 @@ def conv_dgrad(dy, weight, dx, stride, pad, dil, addend=None, mode=0):
     ap, lda = (None, 0) if addend is None else pm(addend)
     ho, wo = conv_out_hw(h, w, kh, kw, stride, pad, dil)
     m = n * ho * wo
-    x6 = CONV_IMPL == "x6" and lddy >= pad4(o)
+    x6 = lddy >= pad4(o)            # else the f32-MFMA kernel of conv_gemm.hip, which takes any dy row stride
     wptr = weight_transpose(weight).data_ptr() if x6 else w_ohwi(weight).data_ptr()
     cost = (2.0 * m * o * cin * kh * kw, 4.0 * (n * h * w * cin * (2 if addend is not None or mode else 1) + m * o + o * cin * kh * kw))
     args = (dyp, lddy, wptr, ap, lda, dxp, lddx, n, h, w, cin, o, kh, kw, stride, pad, dil, mode)
@@ -552,8 +541,6 @@ def conv_dgrad(dy, weight, dx, stride, pad, dil, addend=None, mode=0):
 def conv_dgrad_bnb(dy, weight, g, y_prev, coefs, relu, partials, stride, pad, dil, addend=None, out_prev=None):
     """Input gradient + front half of the producer layer's BatchNorm backward in the dgrad epilogue: g <- relumask * (dx [+ addend]),
     partials[ceil(M/64), 2, Cin] <- (sum g, sum g*xhat) per 64 rows.  -> False when the geometry has no fused kernel."""
-    if CONV_IMPL != "x6":
-        return False
     n, cin, h, w = g.shape
     o, _, kh, kw = weight.shape
     if _B16 and _dgrad_b16(dy, weight, g, stride, pad, dil, addend=addend, bnb=(y_prev, coefs, relu, partials, out_prev)):
@@ -585,8 +572,6 @@ def conv_dgrad_lin(dd, weight, dx, addend=None, bnb=None):
     """1x1 stride-1 input gradient with the dy operand evaluated in the loader from a DeferredDy.  bnb = (y_prev, coefs, partials):
     BatchNorm-backward epilogue for the producer of the conv's input (as conv_dgrad_bnb; dx then receives g).  -> False when the
     geometry has no fused kernel (the caller materialises dy)."""
-    if CONV_IMPL != "x6":
-        return False
     n, cin, h, w = dx.shape
     o = weight.shape[0]
     if _B16 and dd.g.dtype == torch.bfloat16:
@@ -618,12 +603,16 @@ _WS = {}
 
 def workspace(nbytes, device, tag="ws"):
     """Grow-only scratch buffer per (device, tag, launch stream): kernels of one stream run in order, so a buffer is never
-    shared by kernels that may overlap (the weight-gradient stream gets its own)."""
-    key = (device, tag, torch._C._cuda_getCurrentRawStream(device.index if device.index is not None else torch.cuda.current_device())
-           if device.type == "cuda" else 0)
+    shared by kernels that may overlap.  A buffer of the weight-gradient side stream is allocated with that stream as its owner:
+    when a larger one replaces it, the allocator hands the old block out again only to side-stream allocations, which the
+    stream orders after the block's last use (not to the compute stream, which may be ahead of the side stream)."""
+    st = _st()
+    key = (device, tag, st)
     buf = _WS.get(key)
     if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
+        side = _SIDE.get(device.index)
+        with torch.cuda.stream(side) if side is not None and side.cuda_stream == st else contextlib.nullcontext():
+            buf = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
         _WS[key] = buf
     return buf
 
@@ -632,64 +621,50 @@ def workspace(nbytes, device, tag="ws"):
 # read-only inputs, so the two kernels can co-reside on a CU (98 KB + 61 KB of LDS) and fill each other's load / split /
 # epilogue phases and grid tails.  Every hand-scheduled backward node joins the side stream before it returns its gradients
 # (layers.GradMap.ordered / flush), so consumers of p.grad are ordered after the wgrads without knowing about the stream.
+# WGRAD_ASYNC = False (SEGHIERO_WGRAD_STREAM=0, and inside ops.profile()) runs them in order on the compute stream.
 WGRAD_ASYNC = os.environ.get("SEGHIERO_WGRAD_STREAM", "1") != "0"
-WGRAD_NSTREAMS = int(os.environ.get("SEGHIERO_WGRAD_NSTREAMS", "1"))
-WGRAD_AFTER_DGRAD = os.environ.get("SEGHIERO_WGRAD_AFTER_DGRAD", "1") != "0"
-_WG_STREAMS = {}          # device index -> [[streams], [pending flags], next]
+_SIDE = {}                # device index -> its weight-gradient side stream
+_PENDING = False          # work was launched on a side stream since the last join_wgrad()
 
 
-class _WgEnt:
-    def __init__(self, device):
-        self.streams = [torch.cuda.Stream(device=device) for _ in range(max(1, WGRAD_NSTREAMS))]
-        self.pending = [False] * len(self.streams)
-        self.next = 0
-
-    def take(self):
-        k = self.next
-        self.next = (k + 1) % len(self.streams)
-        self.pending[k] = True
-        return k, self.streams[k]
-
-
-def _wgrad_side(device):
-    ent = _WG_STREAMS.get(device.index)
-    if ent is None:
-        ent = _WgEnt(device)
-        _WG_STREAMS[device.index] = ent
-    return ent
-
-
-def _launch_on_side(device, launch, tagfmt, tensors):
-    """launch(tag) with the weight-gradient side stream as the launch stream of its C-ABI calls (ops._STREAM: the kernels take their
-    stream as an argument, so torch's current stream is not switched -- a `with torch.cuda.stream(...)` costs more host time than the
-    launch itself); the side stream first waits for what the compute stream has queued, and the allocator is told about the tensors."""
-    global _STREAM
-    k, st = _wgrad_side(device).take()
-    st.wait_stream(torch.cuda.current_stream(device))     # dy / x were produced on the compute stream
+def _wgrad_launch(side, launch, reads):
+    """-> launch().  side and WGRAD_ASYNC: its C-ABI calls go to the weight-gradient side stream of reads[0]'s device (ops._STREAM:
+    the kernels take their stream as an argument, so torch's current stream is not switched -- a `with torch.cuda.stream(...)`
+    costs more host time than the launch itself); the side stream first waits for what the compute stream has queued, and the
+    allocator is told that the side stream uses `reads` (the operands and the result).  Otherwise launch() runs in order."""
+    global _STREAM, _PENDING
+    if not (side and WGRAD_ASYNC):
+        return launch()
+    dev = reads[0].device
+    st = _SIDE.get(dev.index)
+    if st is None:
+        st = _SIDE[dev.index] = torch.cuda.Stream(device=dev)
+    st.wait_stream(torch.cuda.current_stream(dev))        # dy / x were produced on the compute stream
     prev, _STREAM = _STREAM, st.cuda_stream
     try:
-        launch(tagfmt % k)
+        rc = launch()
     finally:
         _STREAM = prev
-    for t in tensors:
+    for t in reads:
         t.record_stream(st)                                 # the allocator must not recycle them under the side stream
-
+    _PENDING = True
+    return rc
 
 
 def join_wgrad():
-    """Make the current stream wait for every weight gradient launched on the side stream(s) so far."""
-    for idx, ent in _WG_STREAMS.items():
-        for k, st in enumerate(ent.streams):
-            if ent.pending[k]:
-                torch.cuda.current_stream(idx).wait_stream(st)
-                ent.pending[k] = False
+    """Make the current stream wait for every weight gradient launched on the side stream so far."""
+    global _PENDING
+    if _PENDING:
+        for idx, st in _SIDE.items():
+            torch.cuda.current_stream(idx).wait_stream(st)
+        _PENDING = False
 
 
 def wgrad_aff_ok(x, dweight, stride, pad, dil):
     """Can conv_wgrad(..., aff=...) read this x through the producer's BatchNorm + ReLU?  (x6 kernel, output width >= 16)"""
     n, cin, h, w = x.shape
     o, _, kh, kw = dweight.shape
-    return CONV_IMPL == "x6" and _wgrad_pipelined_ok(x, o, kh, kw, stride, pad, dil)
+    return _wgrad_pipelined_ok(x, o, kh, kw, stride, pad, dil)
 
 
 def _wgrad_pipelined_ok(x, o, kh, kw, stride, pad, dil):
@@ -715,7 +690,7 @@ def conv_wgrad(x, dy, dweight, stride, pad, dil, side=False, aff=None):
         dy, dd = dd.materialize(), None                      # the fp32-accurate lin loaders take an fp32 g
     if dd is None:
         dy = f32(dy)
-    if (x.dtype == torch.bfloat16 or dd is not None) and not (CONV_IMPL == "x6" and _wgrad_pipelined_ok(x, o, kh, kw, stride, pad, dil)):
+    if (x.dtype == torch.bfloat16 or dd is not None) and not _wgrad_pipelined_ok(x, o, kh, kw, stride, pad, dil):
         # bf16-stored x / deferred dy where the pipelined wgrad has no instantiation (output width < 16: tiny test inputs; operands
         # of 2 GiB or more): widen / materialise once and run the plain kernel
         if x.dtype == torch.bfloat16:
@@ -727,7 +702,7 @@ def conv_wgrad(x, dy, dweight, stride, pad, dil, side=False, aff=None):
     if dd is not None:
         dy = dd.g
     # tiny output-channel counts (cls_seg, aux head) stay on the f32-MFMA kernel
-    x6 = CONV_IMPL == "x6" and o >= 32 and (cin * kh * kw >= 128 or (cin * kh * kw == 64 and o >= 128))
+    x6 = o >= 32 and (cin * kh * kw >= 128 or (cin * kh * kw == 64 and o >= 128))
     if aff is not None or dd is not None or x.dtype == torch.bfloat16:
         x6 = True
     need = LIB.raw("sh_conv_wgrad_x6_workspace" if x6 else "sh_conv_wgrad_workspace")(n, h, w, cin, o, kh, kw, stride, pad, dil)
@@ -738,30 +713,19 @@ def conv_wgrad(x, dy, dweight, stride, pad, dil, side=False, aff=None):
     ho, wo = conv_out_hw(h, w, kh, kw, stride, pad, dil)
     m = n * ho * wo
     cost = (2.0 * m * o * cin * kh * kw, 4.0 * (n * h * w * cin + m * o + o * cin * kh * kw))
-    name = "sh_conv_wgrad_x6" if x6 else "sh_conv_wgrad"
-
-    def launch(tag="wgrad"):
-        ws = workspace(need, x.device, tag)              # one workspace per stream: its kernels stay in that stream's order
-        if dd is not None:
-            y2p, ldy2, y2b = pmx(dd.y)
-            if not _call_fused("sh_conv_wgrad_x6_lin", xp, ldx, None if aff is None else _rp(aff, 2), None if aff is None else _rp(aff, 3),
-                               dyp, lddy, y2p, ldy2, dd.lin.data_ptr(), dweight.data_ptr(), ws.data_ptr(), n, h, w, cin, o, kh, kw, stride, pad, dil,
-                               xb | (y2b << 1), _st(), cost=cost, key=_ckey(n, h, w, cin, o, kh, stride, dil)):
-                raise SegHieroHipError("sh_conv_wgrad_x6_lin: unsupported geometry (check lin_ok before deferring the BatchNorm-backward apply)")
-            return
-        if aff is not None:
-            if not _call_fused("sh_conv_wgrad_x6_aff", xp, ldx, _rp(aff, 2), _rp(aff, 3), dyp, lddy, dweight.data_ptr(),
-                               ws.data_ptr(), n, h, w, cin, o, kh, kw, stride, pad, dil, xb, _st(), cost=cost,
-                               key=_ckey(n, h, w, cin, o, kh, stride, dil)):
-                raise SegHieroHipError("sh_conv_wgrad_x6_aff: unsupported geometry (check wgrad_aff_ok before deferring the activation)")
-            return
-        _call(name, xp, ldx, dyp, lddy, dweight.data_ptr(), ws.data_ptr(), n, h, w, cin, o, kh, kw, stride, pad, dil, *((xb,) if x6 else ()), _st(),
-              cost=cost, key=_ckey(n, h, w, cin, o, kh, stride, dil))
-
-    if not (side and WGRAD_ASYNC and x.is_cuda):
-        launch()
-        return
-    _launch_on_side(x.device, launch, "wgrad%d", (x, dy, dweight) + (() if dd is None else (dd.y, dd.lin)))
+    aff2, aff3 = (None, None) if aff is None else (_rp(aff, 2), _rp(aff, 3))
+    if dd is not None:
+        y2p, ldy2, y2b = pmx(dd.y)
+        name, head, flags = "sh_conv_wgrad_x6_lin", (xp, ldx, aff2, aff3, dyp, lddy, y2p, ldy2, dd.lin.data_ptr()), (xb | (y2b << 1),)
+    elif aff is not None:
+        name, head, flags = "sh_conv_wgrad_x6_aff", (xp, ldx, aff2, aff3, dyp, lddy), (xb,)
+    else:
+        name, head, flags = ("sh_conv_wgrad_x6", (xp, ldx, dyp, lddy), (xb,)) if x6 else ("sh_conv_wgrad", (xp, ldx, dyp, lddy), ())
+    key = _ckey(n, h, w, cin, o, kh, stride, dil)
+    launch = lambda: _call_fused(name, *head, dweight.data_ptr(), workspace(need, x.device, "wgrad").data_ptr(),
+                                 n, h, w, cin, o, kh, kw, stride, pad, dil, *flags, _st(), cost=cost, key=key)
+    if not _wgrad_launch(side, launch, (x, dy, dweight) + (() if dd is None else (dd.y, dd.lin))):
+        raise SegHieroHipError(f"{name}: unsupported geometry (check lin_ok / wgrad_aff_ok before deferring dy / the activation)")
 
 
 def _wgrad_b16(x, dy, dweight, stride, pad, dil, side, aff):
@@ -786,19 +750,12 @@ def _wgrad_b16(x, dy, dweight, stride, pad, dil, side, aff):
     ho, wo = conv_out_hw(h, w, kh, kw, stride, pad, dil)
     m = n * ho * wo
     cost = (2.0 * m * o * cin * kh * kw, float(2 * n * h * w * cin + (2 if gb else 4) * m * o * (2 if dd is not None else 1) + 4 * o * cin * kh * kw))
-    ok = [True]
-
-    def launch(tag):
-        ws = workspace(need, x.device, tag)
-        ok[0] = _call_fused("sh_conv_wgrad_b16", xp, ldx, None if aff is None else _rp(aff, 2), None if aff is None else _rp(aff, 3),
-                            gp, ldg, ylp, ldyl, None if dd is None else dd.lin.data_ptr(), dweight.data_ptr(), ws.data_ptr(), n, h, w, cin, o,
-                            kh, kw, stride, pad, dil, gb, _st(), cost=cost, key=_ckey(n, h, w, cin, o, kh, stride, dil))
-
-    if not (side and WGRAD_ASYNC and x.is_cuda):
-        launch("wgrad")
-        return ok[0]
-    _launch_on_side(x.device, launch, "wgrad%d", (x, g, dweight) + (() if dd is None else (dd.y, dd.lin)))
-    return ok[0]
+    key = _ckey(n, h, w, cin, o, kh, stride, dil)
+    launch = lambda: _call_fused("sh_conv_wgrad_b16", xp, ldx, None if aff is None else _rp(aff, 2), None if aff is None else _rp(aff, 3),
+                                 gp, ldg, ylp, ldyl, None if dd is None else dd.lin.data_ptr(), dweight.data_ptr(),
+                                 workspace(need, x.device, "wgrad").data_ptr(), n, h, w, cin, o, kh, kw, stride, pad, dil, gb, _st(),
+                                 cost=cost, key=key)
+    return _wgrad_launch(side, launch, (x, g, dweight) + (() if dd is None else (dd.y, dd.lin)))
 
 
 def conv_partials(m, cout, device):
@@ -823,7 +780,7 @@ def dwconv_fprop(x, weight, y, partials, dil, aff=None):
 def dw_lin_ok(shape, dil):
     """Can the depthwise dgrad / wgrad read their dy operand as a DeferredDy?  (strip-walk kernels: dilation 1, H and W multiples of 8)"""
     n, c, h, w = shape
-    return DEFER_APPLY and dil == 1 and h % 8 == 0 and w % 8 == 0 and c % 4 == 0
+    return dil == 1 and h % 8 == 0 and w % 8 == 0 and c % 4 == 0
 
 
 def _lin_args(dy):
@@ -859,19 +816,11 @@ def dwconv_wgrad(x, dy, dweight, dil, side=False, aff=None):
     p = dw_partials_rows(n, h, w)
     xp, ldx, xb = pmx(x)
     largs, yb = _lin_args(dy)
-    dd = dy if isinstance(dy, DeferredDy) else None
-    if dd is not None:
-        dy = dd.g
-
-    def launch(tag="dwwgrad"):
-        ws = workspace(p * 9 * c * 4, x.device, tag)
-        _call("sh_dwconv_wgrad", xp, ldx, None if aff is None else _rp(aff, 2), None if aff is None else _rp(aff, 3),
-              *largs, ws.data_ptr(), dweight.data_ptr(), n, h, w, c, dil, xb | (yb << 1), _st(), key=(None if _PROF is None else f"{n}x{h}x{w} C{c} d{dil}"))
-
-    if not (side and WGRAD_ASYNC and x.is_cuda):
-        launch()
-        return
-    _launch_on_side(x.device, launch, "dwwgrad%d", (x, dy, dweight) + (() if dd is None else (dd.y, dd.lin)))
+    key = None if _PROF is None else f"{n}x{h}x{w} C{c} d{dil}"
+    launch = lambda: _call("sh_dwconv_wgrad", xp, ldx, None if aff is None else _rp(aff, 2), None if aff is None else _rp(aff, 3), *largs,
+                           workspace(p * 9 * c * 4, x.device, "dwwgrad").data_ptr(), dweight.data_ptr(), n, h, w, c, dil, xb | (yb << 1),
+                           _st(), key=key)
+    _wgrad_launch(side, launch, (x, dy.g, dweight, dy.y, dy.lin) if isinstance(dy, DeferredDy) else (x, dy, dweight))
 
 
 # ----------------------------------------------------------------------------- batch norm
@@ -892,7 +841,7 @@ def _all_reduce_sq(sq):
     return sq
 
 
-FOLD_MIN = int(os.environ.get("SEGHIERO_FOLD_MIN", "4096"))      # partial lists at least this long are folded 64:1 before the finalize
+FOLD_MIN = 4096           # partial lists at least this long are folded 64:1 before the finalize
 FOLD_CHUNK = 64
 
 
@@ -989,8 +938,6 @@ def dw_center_wgrad(dgamma, gamma, isy, dw_weight, eps, dweight, g=None, x=None,
 def conv1x1_grouped_fprop(sources, weights, y, partials):
     """One launch for several pointwise convs of one geometry (the ASPP branches): sources = [(x, coefs or None)], group g writes
     y[:, g*A:(g+1)*A].  -> False when the geometry has no grouped kernel."""
-    if CONV_IMPL != "x6":
-        return False
     k = len(sources)
     n, cin, h, w = sources[0][0].shape
     a = weights[0].shape[0]
@@ -1035,9 +982,6 @@ def channel_stats(y):
     yp, ldy = pm(y)
     _call("sh_channel_stats", yp, ldy, m, c, partials.data_ptr(), _st())
     return partials
-
-
-RELU_MASK = os.environ.get("SEGHIERO_RELU_MASK", "1") != "0"      # residual blocks keep a 1/16-size ReLU quad mask of their output for the backward
 
 
 def new_relu_mask(n, c, h, w, device):
@@ -1088,20 +1032,18 @@ class DeferredDy:
         return self._dy
 
 
-DEFER_APPLY = os.environ.get("SEGHIERO_DEFER_APPLY", "1") != "0"     # BatchNorm-backward apply in the 1x1 consumers' loaders
-# The dgrad re-evaluates dy once per 128-column tile of its OUTPUT (Cin / 128 times), the apply pass once: deferring pays where the
+# BatchNorm-backward apply in the 1x1 consumers' loaders (DeferredDy, lin_ok).  The dgrad re-evaluates dy once per 128-column tile of its OUTPUT (Cin / 128 times), the apply pass once: deferring pays where the
 # dy tensor is wide and the dgrad output narrow (Bottleneck conv3: 4P -> P), not the other way round (conv1: P -> 4P).  Deferred
 # when Cout * DEFER_RATIO >= Cin; measured (same-box A/B, ms per step): always 33.85, ratio 1 (also 512 -> 512) 33.7 / 34.0,
 # ratio 0.5 (Cout >= 2 Cin) 33.6 / 33.8 -- the two-stream loader costs the square pointwise convs what the apply pass saved.
-DEFER_RATIO = float(os.environ.get("SEGHIERO_DEFER_RATIO", "0.5"))
+DEFER_RATIO = 0.5
 # bf16 compute mode: a gradient w.r.t. an activation is stored like the activation itself -- bf16 where the forward tensor is bf16
 # (trunk and decoder), fp32 elsewhere -- except where its consumer only takes fp32 (depthwise / pooling / resampling kernels, the
 # fp32-accurate fallbacks): grad_dtype(like, fp32_consumer)
-GRAD_BF16 = os.environ.get("SEGHIERO_GRAD_BF16", "1") != "0"
 
 
 def grad_dtype(like, fp32_consumer=False):
-    if _B16 and GRAD_BF16 and not fp32_consumer and like is not None and like.dtype == torch.bfloat16:
+    if _B16 and not fp32_consumer and like is not None and like.dtype == torch.bfloat16:
         return torch.bfloat16
     return torch.float32
 
@@ -1110,7 +1052,7 @@ def strided_dgrad_b16_ok(weight, cin, stride, pad, dil, scatter):
     """bf16 compute mode: does the one-product kernel take this strided input gradient (so that dy and dx may be bf16 tensors)?
     scatter: the 1x1 strided conv whose gradient is added into an existing dx; otherwise stride-2 KxK by parity class."""
     o, _, kh, kw = weight.shape
-    if not (_B16 and GRAD_BF16 and CONV_IMPL == "x6" and cin % 8 == 0 and o % 8 == 0):
+    if not (_B16 and cin % 8 == 0 and o % 8 == 0):
         return False
     if scatter:
         return kh == 1 and kw == 1 and pad == 0
@@ -1122,9 +1064,7 @@ def lin_ok(x_shape, weight, stride, pad, dil):
     counts, output width >= 16 for the pipelined wgrad, operands below the 2 GiB buffer-descriptor range)"""
     n, cin, h, w = x_shape
     o, _, kh, kw = weight.shape
-    if _B16 and not GRAD_BF16:
-        return False                   # bf16 compute mode: lin(g, y) takes a bf16 g (GRAD_BF16); with fp32 gradients dy is materialised
-    return (DEFER_APPLY and CONV_IMPL == "x6" and kh == 1 and kw == 1 and stride == 1 and pad == 0 and o % 4 == 0 and cin % 4 == 0
+    return (kh == 1 and kw == 1 and stride == 1 and pad == 0 and o % 4 == 0 and cin % 4 == 0
             and o >= 32 and cin >= 64 and w >= 16 and n * h * w * max(pad4(o), pad4(cin)) * 4 < (1 << 31)
             and o * DEFER_RATIO >= cin)
 
@@ -1390,8 +1330,8 @@ def hiera2_fwd(logits, labels8, n_fine, hiera_index, want_coarse=False, want_gra
     return loss, sums, coarse, gw
 
 
-LOSS_BWD_TWO_PASS = os.environ.get("SEGHIERO_LOSS_TWO_PASS", "1") != "0"
-LOSS_FWD_GRAD = os.environ.get("SEGHIERO_LOSS_FWD_GRAD", "1") != "0"    # the loss forward also emits the per-pixel gradient
+LOSS_BWD_TWO_PASS = True  # full-resolution gradient in a workspace, then the resize adjoint (False: the tile kernel, a test reference)
+LOSS_FWD_GRAD = True      # the loss forward also emits the per-pixel gradient (False: the backward computes it, a test reference)
 
 
 def _loss_bwd_ws(n, h, w, H, W, ldd, device):

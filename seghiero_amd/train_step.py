@@ -204,10 +204,9 @@ class SegHieroTrainer:
     def train_step(self, img, fine_mask, epoch=0):
         """One iteration of train.py:260-320.  Returns the (device) loss scalar; nothing is synchronised."""
         self.optimizer.zero_grad(set_to_none=True)
-        if ops.CONV_IMPL == "x6":
-            ops.prepare_dgrad_weights(self._dgrad_weights, self._wt_cache)   # all dgrad operands in 2 launches; valid until SGD
-            if self.compute_dtype == torch.bfloat16:
-                ops.prepare_bf16_weights(self._dgrad_weights, self._wb_cache)    # bf16 operand copies of the fp32 master weights
+        ops.prepare_dgrad_weights(self._dgrad_weights, self._wt_cache)   # all dgrad operands in 2 launches; valid until SGD
+        if self.compute_dtype == torch.bfloat16:
+            ops.prepare_bf16_weights(self._dgrad_weights, self._wb_cache)    # bf16 operand copies of the fp32 master weights
         ops.STEP_SCOPE = self._step_scope            # the loss forward's per-pixel gradient buffers are reused from step to step
         try:
             if self.grad_sync is not None and self.n_super == 0:

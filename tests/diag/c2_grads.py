@@ -16,7 +16,7 @@ lr_, _, _, _ = ref.forward_loss(img, lab, 0); lr_.backward()
 ops.prepare_dgrad_weights(mine._dgrad_weights, mine._wt_cache)
 lm, _, _, _ = mine.forward_loss(img.cuda(), lab.cuda(), 0); lm.backward(); ops.release_dgrad_weights()
 torch.cuda.synchronize()
-print({k: os.environ.get(k) for k in ("SEGHIERO_X6P", "SEGHIERO_FUSE_BN", "SEGHIERO_X6P_VEC", "SEGHIERO_WGRAD_STREAM")}, "loss", float(lm), float(lr_))
+print({k: os.environ.get(k) for k in ("SEGHIERO_X6P", "SEGHIERO_X6P_VEC", "SEGHIERO_WGRAD_STREAM")}, "loss", float(lm), float(lr_))
 rows = []
 for name, m in ref.modules().items():
     pm = dict(mine.modules()[name].named_parameters())

@@ -14,7 +14,7 @@ sum((o * g).sum() for o, g in zip(outs, gs)).backward()
 om = mine(x.cuda()); sum((o * g.cuda()).sum() for o, g in zip(om, gs)).backward()
 rel = lambda a, b: float((a.cpu().double() - b.double()).norm() / b.double().norm())
 pm, pr = dict(mine.named_parameters()), dict(ref.named_parameters())
-print({k: os.environ.get(k) for k in ("SEGHIERO_X6P", "SEGHIERO_FUSE_BN", "SEGHIERO_X6P_VEC")})
+print({k: os.environ.get(k) for k in ("SEGHIERO_X6P", "SEGHIERO_X6P_VEC")})
 for k in ("stem_conv.weight", "stem_bn.weight", "stem_bn.bias", "layer1.0.conv1.weight", "layer2.0.conv1.weight", "layer4.1.conv2.weight"):
     print(f"  {k:28s} {rel(pm[k].grad, pr[k].grad):.2e}")
 for i, (a, b) in enumerate(zip(om, outs)):

@@ -498,8 +498,8 @@ def test_config2_full_size_step0_matches_oracle(sa):
     # batch 2: the image-pool BatchNorm (sep_aspp_contrast_head.py:94-98) then normalises TWO samples per channel -- its output is
     # +-1 whatever the input, its input gradient is a 0/0 limit, and every gradient upstream of c4 moves by ~4 % between ANY two
     # fp32 evaluations (measured with tests/diag/c2_grads.py: identical 4.2e-2 worst relative error against the CPU oracle for the
-    # round-1 kernels, the pipelined kernels and the fused-BatchNorm paths, which agree with EACH OTHER to 2e-6,
-    # tests/diag/fuse_ab.py).  Trunk gradients are pinned per block in test_every_block_in_isolation_matches_torch.
+    # round-1 kernels, the pipelined kernels and the fused-BatchNorm paths, which agreed with EACH OTHER to 2e-6 when the
+    # every-BatchNorm-its-own-pass path still existed to compare against).  Trunk gradients are pinned per block in test_every_block_in_isolation_matches_torch.
     sm, sr = mine.aspp_head.state_dict(), ref.modules()["aspp_head"].state_dict()
     for k in ("cls_seg.weight", "sep_bottleneck.1.pointwise.weight", "sep_bottleneck.0.depthwise.weight", "c1_bottleneck.0.weight"):
         assert relerr(sm[k], sr[k]) < 1e-3, (k, relerr(sm[k], sr[k]))

@@ -391,6 +391,100 @@ def test_dwconv_deferred_batchnorm_backward_apply(ops, shape):
     close(dwb, dwa, 0, 1e-5 * float(dwa.abs().max()), "wgrad, x through its BatchNorm")
 
 
+@pytest.mark.parametrize("operand", ["plain", "aff", "deferred", "aff+deferred"])
+def test_weight_gradients_on_the_side_stream_equal_inline(ops, operand):
+    """conv_wgrad, _wgrad_b16 and dwconv_wgrad launched on the weight-gradient side stream (side=True, then join_wgrad) give
+    BIT-identical weight gradients to the same calls run in order on the compute stream: plain operands, x read through its
+    producer's BatchNorm + ReLU (aff=), dy as a DeferredDy, and both."""
+    assert ops.WGRAD_ASYNC
+    g = torch.Generator().manual_seed(len(operand))
+    n, h, w, cin, cout = 2, 16, 16, 64, 128
+    aff = "aff" in operand
+    deferred = "deferred" in operand
+    rnd = lambda *s: torch.randn(*s, generator=g)
+    coefs = lambda c: torch.stack([0.2 * rnd(c), 0.5 + torch.rand(c, generator=g), rnd(c), 0.3 * rnd(c)]).to(DEV).contiguous()
+    lin = lambda c: torch.stack([0.5 + torch.rand(c, generator=g), 0.3 * rnd(c), 0.2 * rnd(c), 0.1 * rnd(c)]).to(DEV).contiguous()
+
+    def both(run, like):
+        a, b = torch.empty_like(like), torch.empty_like(like)
+        run(a, False)
+        run(b, True)
+        ops.join_wgrad()
+        torch.cuda.synchronize()
+        assert torch.equal(a, b), operand
+
+    # fp32-accurate dense conv: 1x1 (the deferred / loader paths) and 3x3 (the plain and aff paths)
+    x = nhwc(rnd(n, cin, h, w))
+    pc = coefs(cin) if aff else None
+    dy = nhwc(rnd(n, cout, h, w))
+    if deferred:
+        dy = ops.DeferredDy(dy, nhwc(rnd(n, cout, h, w)), lin(cout), None, None, None)
+    like = wl(torch.empty(cout, cin, 1, 1))
+    both(lambda dw, side: ops.conv_wgrad(x, dy, dw, 1, 0, 1, side=side, aff=pc), like)
+    if not deferred:
+        like3 = wl(torch.empty(cout, cin, 3, 3))
+        both(lambda dw, side: ops.conv_wgrad(x, dy, dw, 1, 1, 1, side=side, aff=pc), like3)
+    # bf16 compute mode
+    xb = nhwc_bf16(rnd(n, cin, h, w))
+    gb = nhwc_bf16(rnd(n, cout, h, w))
+    dyb = ops.DeferredDy(gb, nhwc_bf16(rnd(n, cout, h, w)), lin(cout), None, None, None) if deferred else gb
+
+    def b16(dw, side, pad):
+        assert ops._wgrad_b16(xb, dyb, dw, 1, pad, 1, side, pc)
+    both(lambda dw, side: b16(dw, side, 0), like)
+    if not deferred:
+        both(lambda dw, side: b16(dw, side, 1), like3)
+    # depthwise (strip-walk kernels)
+    c = 128
+    xd = nhwc(rnd(n, c, h, w))
+    pcd = coefs(c) if aff else None
+    dyd = nhwc(rnd(n, c, h, w))
+    if deferred:
+        dyd = ops.DeferredDy(dyd, nhwc(rnd(n, c, h, w)), lin(c), None, None, None)
+    both(lambda dw, side: ops.dwconv_wgrad(xd, dyd, dw, 1, side=side, aff=pcd), torch.empty((c, 1, 3, 3), device=DEV))
+
+
+def test_side_stream_workspace_is_not_reused_by_the_compute_stream(ops):
+    """A side-stream weight gradient whose workspace is replaced by a larger one (the grow-only ops.workspace) while it is still
+    queued behind other side-stream work: the retired block must not be handed to a compute-stream allocation before the side
+    stream has passed its last use.  Before the workspace was allocated with the side stream as its owner, the allocator returned
+    it to the compute stream's pool at once: the probe below received the same block and the wgrad's partial slabs overwrote it."""
+    assert ops.WGRAD_ASYNC
+    from seghiero_amd._lib import LIB
+    c, h, w = 256, 64, 64
+    nbytes = lambda n: LIB.raw("sh_dw_partials")(n, h, w) * 9 * c * 4
+    small = nbytes(2)
+    assert small > 1 << 20 and nbytes(4) > small       # no 1 MiB minimum rounding: the first launch writes its whole buffer
+    g = torch.Generator().manual_seed(5)
+    x1, dy1 = nhwc(torch.randn(2, c, h, w, generator=g)), nhwc(torch.randn(2, c, h, w, generator=g))
+    x2, dy2 = nhwc(torch.randn(4, c, h, w, generator=g)), nhwc(torch.randn(4, c, h, w, generator=g))
+    wt = lambda: torch.empty((c, 1, 3, 3), device=DEV)
+    ref1, ref2, dw1, dw2 = wt(), wt(), wt(), wt()
+    ops.dwconv_wgrad(x2, dy2, dw2, 1, side=True)        # (creates the side stream)
+    ops.join_wgrad()
+    torch.cuda.synchronize()
+    ops._WS.clear()                                      # fresh grow-only workspaces from here on
+    side = ops._SIDE[torch.device(DEV).index]
+    with torch.cuda.stream(side):
+        torch.cuda._sleep(100_000_000)                   # holds the side stream for tens of milliseconds
+    ops.dwconv_wgrad(x1, dy1, dw1, 1, side=True)        # first workspace: written once the sleep has ended
+    (retired,) = [b for k, b in ops._WS.items() if k[1] == "dwwgrad"]
+    lo, hi = retired.data_ptr(), retired.data_ptr() + retired.numel()
+    assert retired.numel() == small
+    del retired
+    ops.dwconv_wgrad(x2, dy2, dw2, 1, side=True)        # grows the workspace: the first one is retired
+    probe = torch.empty(small, dtype=torch.uint8, device=DEV)       # the compute stream is not waiting for the side stream
+    probe.fill_(0x5A)
+    p0 = probe.data_ptr()
+    assert p0 + small <= lo or p0 >= hi, "a compute-stream tensor was handed the retired side-stream workspace"
+    ops.join_wgrad()
+    torch.cuda.synchronize()
+    assert bool((probe == 0x5A).all()), "the retired workspace was written after the compute stream reused it"
+    ops.dwconv_wgrad(x1, dy1, ref1, 1)
+    ops.dwconv_wgrad(x2, dy2, ref2, 1)
+    assert torch.equal(dw1, ref1) and torch.equal(dw2, ref2)
+
+
 @pytest.mark.parametrize("shape", [(4, 64, 12, 12), (2, 9, 7, 5), (16, 32, 1, 1)])
 @pytest.mark.parametrize("relu,res", [(True, False), (True, True), (False, False)])
 def test_batchnorm_train_fwd_bwd(ops, shape, relu, res):
